@@ -5,6 +5,8 @@
                                                             own ranks - a fresh `python -m torch.distributed.run` child - and
                                                             relays rank 0's JSON line and the child's exit code)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W     (the same ranks)
+    python bench.py ... --dump-outputs DIR                  (also write a fixed sample of the last timed step's score matrix
+                                                            to DIR/*.npy: dump_outputs())
 
 A "step" = one pass of the scoring hot path over the whole synthetic TVR-shaped workload (config C2,
 SURVEY.md 8d): normalise + pack the 10,895 x 2 query vectors, score them against the resident bf16
@@ -90,6 +92,27 @@ def recalls(scores, gt):
     g = scores.gather(1, gt.unsqueeze(1))
     rank = 1 + (scores > g).sum(1)
     return [round(100.0 * (rank <= k).float().mean().item(), 3) for k in (1, 5, 10, 100)]
+
+
+DUMP_ROWS, DUMP_PAIRS, DUMP_SEED = 256, 1 << 20, 12345
+
+
+def dump_outputs(out_dir, fused):
+    """--dump-outputs: what the timed step handed its caller in the last step - the fused (Nq, Nv) fp32 score matrix (950 MB at
+    C2) - as a fixed sample that two builds can compare value for value: DUMP_ROWS whole query rows and DUMP_PAIRS single
+    (query, video) entries spread over the whole matrix, both drawn from a CPU generator seeded with DUMP_SEED (the same
+    positions for every build and rank count), with their positions as float64 (exact).  ~34 MB in all."""
+    import numpy as np
+    nq, nv = fused.shape
+    gen = torch.Generator().manual_seed(DUMP_SEED)
+    rows = torch.randperm(nq, generator=gen)[:min(DUMP_ROWS, nq)].sort().values
+    flat = torch.randint(0, nq * nv, (DUMP_PAIRS,), generator=gen, dtype=torch.int64).sort().values
+    rows_d, flat_d = rows.to(fused.device), flat.to(fused.device)
+    arrays = {"fused_rows": fused.index_select(0, rows_d), "fused_rows_index": rows.double(),
+              "fused_pairs": fused.reshape(-1).index_select(0, flat_d), "fused_pairs_index": flat.double()}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.cpu().numpy())
 
 
 def cpu_baseline(gs, mask, qs, fused_gpu, nq_s=500, nv_s=8718):
@@ -441,11 +464,12 @@ def mfma_sustained():
         return None
 
 
-def run_sharded(cfg, dev, rank, world, comm, steps, warmup):
+def run_sharded(cfg, dev, rank, world, comm, steps, warmup, dump_dir=None):
     """One workload through dist.OverlappedShardScorer (what --gpus N runs): the gallery cut by video, ONE scorer launch per
     step whose query ranges complete in order, per-range finish on a side stream + RCCL all_gather (comm.RcclComm: one enqueue per
     range on the collectives' stream).  Runs on every rank;
-    returns the measurements (rank 0 adds the self-checks: recalls of the ASSEMBLED matrix and a sampled recompute)."""
+    returns the measurements (rank 0 adds the self-checks: recalls of the ASSEMBLED matrix and a sampled recompute; with dump_dir it
+    also writes the sample of that matrix dump_outputs() takes)."""
     from dldkd_amd import dist as ddist
     from dldkd_amd import scoring
     nq, nv = cfg["nq"], cfg["nv"]
@@ -489,6 +513,8 @@ def run_sharded(cfg, dev, rank, world, comm, steps, warmup):
            "flops_per_step_all_ranks": 2.0 * D * NB * nq * float(_lens_all(cfg).sum().item())}
     if rank == 0:
         full = overlap.assemble(nv)                                   # (nq, nv) fp32 as every rank holds it after the gathers
+        if dump_dir:
+            dump_outputs(dump_dir, full)
         res["recall_hip"] = dict(zip(("R@1", "R@5", "R@10", "R@100"), recalls(full, gt)))
         # sampled recompute: one BLK-video block out of every rank's shard (the last one ends at the last video), scored by a
         # plain one-launch scorer call on THIS rank from re-generated clips, against the same columns of the assembled matrix
@@ -683,7 +709,11 @@ def main():
     ap.add_argument("--no-extras", action="store_true")
     ap.add_argument("--launch-timeout", type=float, default=3600.0,
                     help="N > 1 self-launch only: seconds before the launched ranks are killed (a hang must not outlive the lease)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed sample of the last step's fused score matrix to DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # nobody started our ranks: do it ourselves, as a child process, BEFORE anything in this process touches a GPU
@@ -717,7 +747,7 @@ def main():
 
     if comm is not None:
         # ---- N ranks (or the one-rank test hook): the sharded step, self-verified, then the C4 workload the same way
-        r2 = run_sharded(C2, dev, rank, world, comm, a.steps, a.warmup)
+        r2 = run_sharded(C2, dev, rank, world, comm, a.steps, a.warmup, dump_dir=a.dump_outputs)
         r4 = run_sharded(C4, dev, rank, world, comm, max(min(a.steps, 20), 1), max(min(a.warmup, 3), 1)) if not a.no_extras else None
         r5 = run_c5_ddp(dev, rank, world, comm, max(min(a.steps, 20), 2), max(min(a.warmup, 5), 3)) if not a.no_extras else None
         if rank == 0:
@@ -788,7 +818,9 @@ def main():
             fused = step(i)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        kern_ms = sum(s_.elapsed_time(e) for s_, e in ev) / max(a.steps, 1)
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, fused)
+        kern_ms = sum(s_.elapsed_time(e) for s_, e in ev) / a.steps
         achieved = flops_launch / (kern_ms * 1e-3) / 1e12
         # HBM bytes per launch of the dominant kernel: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes,
         # KiB units; FETCH_SIZE doubled per the gfx950 note in MI355X_MICROARCH.md section HBM) from the committed

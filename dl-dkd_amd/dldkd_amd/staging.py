@@ -6,6 +6,7 @@ masks.  A pageable `tensor.to(device)` blocks the host until the stream has drai
 buffer races with the host, which runs several steps ahead of the GPU and would overwrite the buffer before the copy engine has
 read it.  PinnedRing hands out pinned slots round robin and remembers, per slot, an event recorded after the slot's copy was
 enqueued: a slot is only handed out again once that copy has executed (normally long ago, so the wait is free)."""
+import os
 import time
 
 import torch
@@ -57,6 +58,14 @@ class PinnedRing:
             ev = torch.cuda.Event()
             ev.record()
             self.events[self.i] = ev
+
+
+def hardware_queues():
+    """The number of hardware queues HIP spreads this process's streams over on a device: GPU_MAX_HW_QUEUES, default 4."""
+    try:
+        return max(1, int(os.environ.get("GPU_MAX_HW_QUEUES", "4")))
+    except ValueError:
+        return 4
 
 
 def concurrent_streams(device, n, candidates=16, cycles=1_000_000, high_priority=0):
